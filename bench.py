@@ -7,9 +7,16 @@ synthetic tuples: 1,000,000 per GPU (32-byte SHA-256 digests, distinct key per t
 rank r owns tuples [r*N, (r+1)*N) — no data-path collective (there is nothing to reduce;
 SURVEY.md 8(e)); a barrier brackets the timed region and the time is the max over ranks.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--n TUPLES]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--n TUPLES] [--dump-outputs DIR] [--full]
   N>1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 Prints ONE JSON line on rank 0 (fields: see DESIGN.md "Measurement").
+
+A plain run does only what the headline figure needs: workload set-up, warm-up, the timed steps
+(with the full-size parity count and the verify kernel's own HIP-event time taken from those
+same steps), --dump-outputs if given, the result line. Every other leg -- CPU baselines, the
+pipelined / torch-free / host-buffer rates of config 2, config 5 hashing, the adversarial
+batches, configs 3/4 latency, the multi-GPU latency split -- runs only with --full (where the
+--no-* options still switch single legs off).
 """
 from __future__ import annotations
 
@@ -43,6 +50,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5,
                     help="untimed steps: the first full-size dispatches after start-up run ~15%% slower")
     ap.add_argument("--n", type=int, default=1_000_000, help="tuples per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: CPU baselines, pipelined / torch-free / "
+                         "host-buffer rates, config 5 hashing, adversarial batches, configs 3/4 latency")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the verdict "
+                         "arrays verify_dev filled) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-sample", type=int, default=131072)
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads for the CPU baselines (0 = every core this job may use: "
@@ -119,6 +132,25 @@ def _openssl_rate(tuples: np.ndarray, threads: int, seconds: float, runs: int = 
         return json.loads(out.stdout.strip().splitlines()[-1])
     finally:
         os.unlink(path)
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: every file of a run together
+
+
+def dump_outputs(path: str, oks, first_lane: int, total_lanes: int) -> None:
+    """--dump-outputs: the verdict array each lane's last timed step filled (what a caller of
+    sbft_gv_verify_p256_dev receives: 1 = valid, 0 = rejected, one per tuple), as float32 .npy.
+    One lane in all writes verdicts.npy, several write verdicts_gpu<k>.npy (k = rank * lanes +
+    lane). An array over its share of the byte budget is cut to a fixed, seeded sample of its
+    tuples (sorted indices from default_rng(0), the same for every run of the same --n)."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // total_lanes // 4 - 64  # float32 elements per file, header included
+    for j, o in enumerate(oks):
+        a = o.cpu().numpy()
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))]
+        name = "verdicts.npy" if total_lanes == 1 else f"verdicts_gpu{first_lane + j}.npy"
+        np.save(os.path.join(path, name), a.astype(np.float32))
 
 
 def _mapped(pattern: str) -> list:
@@ -768,6 +800,8 @@ def main():
         dist.barrier()
         elapsed, mismatches = reduce_timing(elapsed, mismatches,
                                             device=dev if args.dist_backend == "nccl" else None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, oks, rank * len(lanes), world * len(lanes))
     step_ms = [s.elapsed_time(e) for s, e in zip(starts, ends)]
     avg_step_gpu_ms = sum(step_ms) / len(step_ms)
     launches, kern_total_ms = gv.kernel_time()
@@ -857,7 +891,8 @@ def main():
             rec["metric"] = "P-256 ECDSA verifies/sec (multi-device rehearsal on one GPU)"
             rec["config"]["logical_slots"] = slots
             rec["config"]["parallelism"] = f"in-process, {slots} engine slots on 1 GPU (rehearsal, no scaling claim)"
-        if n_gpus == 1 and not rehearsal and not args.no_cpu_baseline:
+        full = args.full  # every leg below is beside the headline figure
+        if full and n_gpus == 1 and not rehearsal and not args.no_cpu_baseline:
             cpu_threads = args.cpu_threads or host_cores()["cores_available"]
             base, port, ok_cpu = cpu_baseline(wl, args.cpu_sample, cpu_threads)
             if base:
@@ -866,9 +901,9 @@ def main():
             rec["cpu_oracle"] = port
             rec["parity"]["oracle_sample_mismatches"] = int(
                 (ok[:len(ok_cpu)].cpu().numpy() != ok_cpu).sum())
-        if n_gpus == 1 and not rehearsal and S == 1 and not args.no_pipelined:
+        if full and n_gpus == 1 and not rehearsal and S == 1 and not args.no_pipelined:
             rec["pipelined"] = pipelined(gv, wl, dev, args.steps)
-        if n_gpus == 1 and not rehearsal and S == 1:
+        if full and n_gpus == 1 and not rehearsal and S == 1:
             # the same config-2 measurement without torch, on the HIP runtime the engine ships with
             # (tools/config2_harness: engine-generated workload staged once in HBM, the C ABI's
             # device-resident verify on one stream); value above runs on torch's libamdhip64
@@ -880,11 +915,11 @@ def main():
                 if "verifies_per_s" in tf:
                     tf["vs_torch_process_value"] = round(tf["verifies_per_s"] / value, 4)
                 rec["torch_free_config2"] = tf
-        if world == 1 and not args.no_host_path:
+        if full and world == 1 and not args.no_host_path:
             rec["host_buffer_path"] = host_path(gv, wls, dev)
-        if n_gpus == 1 and not rehearsal and not args.no_sha:
+        if full and n_gpus == 1 and not rehearsal and not args.no_sha:
             rec["sha256_config5"] = sha_config5(gv, dev, args.sha_messages)
-        if n_gpus == 1 and not rehearsal and not args.no_latency:
+        if full and n_gpus == 1 and not rehearsal and not args.no_latency:
             rec["adversarial"] = adversarial(gv, dev)
             lat = latency_configs(gv, args.latency_calls)
             if not args.no_cpu_baseline:
@@ -927,7 +962,7 @@ def main():
                             h["speedup_p50_vs_cpu_thread_per_vote"] = round(q67["p50_ms"] / h["p50_ms"], 2)
                             h["speedup_p99_vs_cpu_thread_per_vote"] = round(q67["p99_ms"] / h["p99_ms"], 2)
             rec["latency"] = lat
-        if (world > 1 or len(devs) > 1) and not rehearsal and not args.no_latency:
+        if full and (world > 1 or len(devs) > 1) and not rehearsal and not args.no_latency:
             # config 3 split over the node's GPUs, measured on the hardware (no
             # multi-GPU run of it existed)
             try:

@@ -14,5 +14,5 @@ step() {  # name, seconds, command...
 rm -f gpurun_out/round.log
 step tests 600 python -u -m pytest tests -m gpu -q -x --timeout 120 --timeout-method thread || exit $?
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
-step bench 600 python bench.py ${BENCH_ARGS} || exit $?
+step bench 600 python bench.py --full ${BENCH_ARGS} || exit $?
 echo "== done" | tee -a gpurun_out/round.log

@@ -19,5 +19,5 @@ else
 fi
 [ -n "$NO_BENCH" ] && exit 0
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
-step bench 600 python bench.py ${BENCH_ARGS} || exit $?
+step bench 600 python bench.py --full ${BENCH_ARGS} || exit $?
 echo "== done" | tee -a gpurun_out/round.log

@@ -15,7 +15,7 @@ step() {  # name, seconds, command...
 step tests 900 python -m pytest tests -m gpu -q --maxfail=5; rc=$?
 [ $rc -gt 1 ] && exit $rc
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
-step bench 600 python bench.py || exit $?
+step bench 600 python bench.py --full || exit $?
 for lib in tools/variants/*.so; do
   [ -e "$lib" ] || continue
   SBFT_GV_LIB=$PWD/$lib step var_$(basename $lib .so) 300 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-latency --no-sha --no-host-path --no-pipelined || exit $?
