@@ -206,6 +206,58 @@ int sbft_gv_sha256_verify_p256_dev(sbft_gv_ctx* ctx, int device, const void* d_b
                                    const void* d_qy, size_t n, void* d_ok, void* d_dig,
                                    void* stream);
 
+/* ---- Ed25519 (the second scheme Fabric 3.x's BFT orderer accepts next to P-256) ----
+ * Batched verification with the verdicts of Go 1.24's crypto/ed25519.Verify, bit for bit.
+ * ok_out[k] = 1 exactly when all of these hold for tuple k:
+ *  1. A = Point.SetBytes(pub) succeeds: y is the low 255 bits of the 32 little-endian bytes,
+ *     reduced mod p = 2^255 - 19 (a non-canonical y >= p is accepted); x is the square-root
+ *     ratio of (y^2 - 1) / (d y^2 + 1), no root: reject; the non-negative root is taken and
+ *     negated if bit 255 is set (x = 0 with the sign bit set is accepted and stays 0).
+ *     Small-order and mixed-order keys are not rejected.
+ *  2. S = sig[32:64], a little-endian integer, is < L = 2^252 + 27742317777372353535851937790883648493.
+ *  3. k = SHA-512(sig[0:32] || pub || msg), a 512-bit little-endian integer, mod L. The hash is
+ *     over the bytes as given, not over re-encoded points.
+ *  4. R' = [S]B - [k]A. There is no cofactor multiplication.
+ *  5. The canonical 32-byte encoding of R' equals sig[0:32] as bytes: a signature whose R is
+ *     non-canonical (y >= p, or x = 0 with the sign bit set) is always rejected. R is never
+ *     decoded.
+ * sig: n x 64 bytes (R || S), pub: n x 32 bytes, as Go's []byte hold them (little-endian).
+ * Message k is blob[off[k], off[k] + len[k]) at any byte alignment; a message outside the blob
+ * is SBFT_GV_EINVAL (and nothing is written). n = 0 returns SBFT_GV_OK; NULL arguments and
+ * n > 2^32 - 1 return SBFT_GV_EINVAL. One launch per share, one lane per signature; any length
+ * is correct, the target is messages of up to a few hundred bytes (one lane hashes its message
+ * alone). Replaces n calls of crypto/ed25519.Verify made by an api.Verifier's
+ * VerifyConsenterSig / VerifyRequest (pkg/api/dependencies.go:54-71) for Ed25519 identities.
+ * Not provided for Ed25519: the plugin layer (sbft_verifier.h), the Go binding,
+ * registered-key tables, a several-lanes-per-signature latency kernel. */
+int sbft_gv_verify_ed25519(sbft_gv_ctx* ctx, const uint8_t* blob, size_t blob_len, const uint64_t* off,
+                           const uint32_t* len, const uint8_t* sig, const uint8_t* pub, size_t n,
+                           uint8_t* ok_out);
+/* Device-resident form: enqueues on the caller's stream and returns. The kernel reads only the
+ * aligned 4-byte words that hold at least one message byte, so a blob allocated at exactly the
+ * sum of its messages' lengths is safe (no over-read slack). d_sig and d_pub must be 4-byte
+ * aligned. The table workspace (1,152 B per lane, at most 262,144 lanes) is kept per caller
+ * stream inside the context. Offsets are not checked here (sbft_gv_sha256_dev's contract). */
+int sbft_gv_verify_ed25519_dev(sbft_gv_ctx* ctx, int device, const void* d_blob, const void* d_off,
+                               const void* d_len, const void* d_sig, const void* d_pub, size_t n, void* d_ok,
+                               void* stream);
+/* Batched SHA-512, one lane per message: dig_out is n x 64 bytes (crypto/sha512.Sum512). */
+int sbft_gv_sha512(sbft_gv_ctx* ctx, const uint8_t* blob, size_t blob_len, const uint64_t* off,
+                   const uint32_t* len, size_t n, uint8_t* dig_out);
+/* Element-wise self-test of the Ed25519 device primitives (diagnostics). a, b, out: n x 32
+ * bytes little-endian; field operands are taken as full 256-bit integers mod p, results are
+ * canonical. */
+#define SBFT_GV_ED_OP_FE_MUL 0        /* a b mod p */
+#define SBFT_GV_ED_OP_FE_SQR 1        /* a^2 mod p */
+#define SBFT_GV_ED_OP_FE_INVERT 2     /* a^-1 mod p (0 for a = 0) */
+#define SBFT_GV_ED_OP_DECODE 3        /* x of the point a encodes, or all-ones if it is none */
+#define SBFT_GV_ED_OP_SC_REDUCE 4     /* (a + 2^256 b) mod L */
+#define SBFT_GV_ED_OP_BASE_MULT 5     /* encoding of [a]B */
+#define SBFT_GV_ED_OP_DOUBLE_SCALAR 6 /* encoding of [a]B + [b]P0, P0 = [SBFT_ED_P0_SCALAR]B a fixed
+                                         non-base point (tools/gen_ed25519_tables.py) */
+int sbft_gv_selftest_ed25519(sbft_gv_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, size_t n,
+                             uint8_t* out);
+
 /* Batched key derivation + ECDSA signing with caller-supplied nonces (the api.Signer side,
  * pkg/api/dependencies.go:46-52; also the synthetic-workload generator). For each k:
  * Q = d*G (qx, qy), r = x(k*G) mod n, s = k^-1 (digest + r d) mod n; status[k] = 1 on

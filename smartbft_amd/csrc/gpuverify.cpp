@@ -1043,6 +1043,26 @@ int sbft_gv_sign_p256_dev(sbft_gv_ctx* ctx, int device, const void* d_d, const v
                : SBFT_GV_OK;
 }
 
+int sbft_gv_verify_ed25519_dev(sbft_gv_ctx* ctx, int device, const void* d_blob, const void* d_off,
+                               const void* d_len, const void* d_sig, const void* d_pub, size_t n, void* d_ok,
+                               void* stream) {
+    if (!ctx || (n && (!d_blob || !d_off || !d_len || !d_sig || !d_pub || !d_ok))) return SBFT_GV_EINVAL;
+    if (n > 0xffffffffu || (((uintptr_t)d_sig | (uintptr_t)d_pub) & 3)) return SBFT_GV_EINVAL;
+    Slot* sl = slot_for(ctx, device);
+    if (!sl) return SBFT_GV_ENODEV;
+    if (n == 0) return SBFT_GV_OK;
+    if (hipSetDevice(device) != hipSuccess) return SBFT_GV_EDEVICE;
+    // the per-lane tables of A's multiples: the stream's workspace (shared, in stream order,
+    // with the other device-resident entry points called on this stream)
+    uint32_t* work = sl->stream_workspace((hipStream_t)stream, sbft_ed25519_work_bytes(n));
+    if (!work) return SBFT_GV_ENOMEM;
+    return sbft_launch_ed25519_verify((const uint8_t*)d_blob, (const uint64_t*)d_off, (const uint32_t*)d_len,
+                                      (const uint8_t*)d_sig, (const uint8_t*)d_pub, (uint8_t*)d_ok, (uint32_t)n,
+                                      work, (hipStream_t)stream)
+               ? SBFT_GV_ELAUNCH
+               : SBFT_GV_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------- host buffers
@@ -1432,6 +1452,78 @@ int enqueue_selftest(const Chunk& c, int op, const uint8_t* a, const uint8_t* b,
     return SBFT_GV_OK;
 }
 
+// ---- Ed25519 / SHA-512 (ed25519_verify.hip) ----
+// Messages [c.begin, +c.count) of a host batch: every [off, off + len) inside the blob (compared
+// without forming off + len, which wraps for an offset near 2^64), the span they cover and the
+// offsets rebased to its start (kept alive by the caller until the stream is synchronised).
+int ed_rebase(const Chunk& c, size_t blob_len, const uint64_t* off, const uint32_t* len,
+              std::vector<uint64_t>& rebased, uint64_t& lo, size_t& span) {
+    uint64_t hi = 0;
+    lo = UINT64_MAX;
+    for (size_t k = c.begin; k < c.begin + c.count; ++k) {
+        if (off[k] > blob_len || len[k] > blob_len - off[k]) return SBFT_GV_EINVAL;
+        lo = std::min(lo, off[k]);
+        hi = std::max(hi, off[k] + len[k]);
+    }
+    rebased.resize(c.count);
+    for (size_t k = 0; k < c.count; ++k) rebased[k] = off[c.begin + k] - lo;
+    span = c.count ? (size_t)(hi - lo) : 0;
+    return SBFT_GV_OK;
+}
+
+// blob | off | len | out rows [| sig | pub | table workspace]: sig == nullptr hashes only
+// (64-byte digests), else verifies (verdict bytes). The blob is staged with no slack: the
+// kernels read only aligned words that hold message bytes.
+int enqueue_ed25519(const Chunk& c, const uint8_t* blob, size_t blob_len, const uint64_t* off,
+                    const uint32_t* len, const uint8_t* sig, const uint8_t* pub, uint8_t* out,
+                    std::vector<uint64_t>& rebased) {
+    Slot* sl = c.slot;
+    uint64_t lo;
+    size_t span;
+    int rc = ed_rebase(c, blob_len, off, len, rebased, lo, span);
+    if (rc || c.count == 0) return rc;
+    const bool verify = sig != nullptr;
+    const size_t row = verify ? 1 : 64;
+    const size_t fb = align_up(span + 4, 256), fo = align_up(8 * c.count, 256), fl = align_up(4 * c.count, 256);
+    const size_t fr = align_up(row * c.count, 256), fs = align_up(64 * c.count, 256), fp = align_up(32 * c.count, 256);
+    HIPCHK(hipSetDevice(sl->device));
+    rc = sl->reserve(fb + fo + fl + fr + (verify ? fs + fp + sbft_ed25519_work_bytes(c.count) : 0));
+    if (rc) return rc;
+    uint8_t* b = sl->dbuf;
+    uint8_t *d_blob = b, *d_off = b + fb, *d_len = d_off + fo, *d_out = d_len + fl, *d_sig = d_out + fr;
+    uint8_t *d_pub = d_sig + fs, *d_work = d_pub + fp;
+    if (span) HIPCHK(hipMemcpyAsync(d_blob, blob + lo, span, hipMemcpyHostToDevice, sl->stream));
+    HIPCHK(hipMemcpyAsync(d_off, rebased.data(), 8 * c.count, hipMemcpyHostToDevice, sl->stream));
+    HIPCHK(hipMemcpyAsync(d_len, len + c.begin, 4 * c.count, hipMemcpyHostToDevice, sl->stream));
+    if (verify) {
+        HIPCHK(hipMemcpyAsync(d_sig, sig + 64 * c.begin, 64 * c.count, hipMemcpyHostToDevice, sl->stream));
+        HIPCHK(hipMemcpyAsync(d_pub, pub + 32 * c.begin, 32 * c.count, hipMemcpyHostToDevice, sl->stream));
+        if (sbft_launch_ed25519_verify(d_blob, (const uint64_t*)d_off, (const uint32_t*)d_len, d_sig, d_pub, d_out,
+                                       (uint32_t)c.count, d_work, sl->stream))
+            return SBFT_GV_ELAUNCH;
+    } else if (sbft_launch_sha512(d_blob, (const uint64_t*)d_off, (const uint32_t*)d_len, d_out, (uint32_t)c.count,
+                                  sl->stream)) {
+        return SBFT_GV_ELAUNCH;
+    }
+    HIPCHK(hipMemcpyAsync(out + row * c.begin, d_out, row * c.count, hipMemcpyDeviceToHost, sl->stream));
+    return SBFT_GV_OK;
+}
+
+int enqueue_selftest_ed25519(const Chunk& c, int op, const uint8_t* a, const uint8_t* b, uint8_t* out) {
+    Slot* sl = c.slot;
+    const size_t f = align_up(32 * c.count, 256);
+    HIPCHK(hipSetDevice(sl->device));
+    int rc = sl->reserve(3 * f + sbft_ed25519_selftest_work_bytes(c.count));
+    if (rc) return rc;
+    uint8_t* d = sl->dbuf;
+    HIPCHK(hipMemcpyAsync(d, a + 32 * c.begin, 32 * c.count, hipMemcpyHostToDevice, sl->stream));
+    HIPCHK(hipMemcpyAsync(d + f, b + 32 * c.begin, 32 * c.count, hipMemcpyHostToDevice, sl->stream));
+    if (sbft_launch_ed25519_selftest(op, d, d + f, d + 2 * f, (uint32_t)c.count, d + 3 * f, sl->stream))
+        return SBFT_GV_ELAUNCH;
+    HIPCHK(hipMemcpyAsync(out + 32 * c.begin, d + 2 * f, 32 * c.count, hipMemcpyDeviceToHost, sl->stream));
+    return SBFT_GV_OK;
+}
+
 // Each device chunk is enqueued and synchronised by its own host thread (for_each_device);
 // a chunk's slot is locked by the thread that drives it.
 // One device's share of a split VerifyProposal (the multi-device branch of
@@ -1591,6 +1683,47 @@ int sbft_gv_sha256(sbft_gv_ctx* ctx, const uint8_t* blob, size_t blob_len, const
         return enqueue_hash(c, blob, blob_len, off, len, nullptr, nullptr, nullptr, nullptr, nullptr,
                             dig_out, rebased[i]);
     });
+}
+
+// every message of the batch inside the blob, before any share is enqueued (so a bad record
+// leaves every output untouched, whichever share it falls in)
+static bool ed_batch_in_bounds(size_t blob_len, const uint64_t* off, const uint32_t* len, size_t n) {
+    for (size_t k = 0; k < n; ++k)
+        if (off[k] > blob_len || len[k] > blob_len - off[k]) return false;
+    return true;
+}
+
+int sbft_gv_verify_ed25519(sbft_gv_ctx* ctx, const uint8_t* blob, size_t blob_len, const uint64_t* off,
+                           const uint32_t* len, const uint8_t* sig, const uint8_t* pub, size_t n,
+                           uint8_t* ok_out) {
+    if (!ctx) return SBFT_GV_EINVAL;
+    if (n == 0) return SBFT_GV_OK;
+    if ((!blob && blob_len) || !off || !len || !sig || !pub || !ok_out || n > 0xffffffffu) return SBFT_GV_EINVAL;
+    if (!ed_batch_in_bounds(blob_len, off, len, n)) return SBFT_GV_EINVAL;
+    std::vector<std::vector<uint64_t>> rebased(ctx->slots.size() + 1);
+    return run_chunks(ctx, n, [&](const Chunk& c, size_t i) {
+        return enqueue_ed25519(c, blob, blob_len, off, len, sig, pub, ok_out, rebased[i]);
+    });
+}
+
+int sbft_gv_sha512(sbft_gv_ctx* ctx, const uint8_t* blob, size_t blob_len, const uint64_t* off,
+                   const uint32_t* len, size_t n, uint8_t* dig_out) {
+    if (!ctx) return SBFT_GV_EINVAL;
+    if (n == 0) return SBFT_GV_OK;
+    if ((!blob && blob_len) || !off || !len || !dig_out || n > 0xffffffffu) return SBFT_GV_EINVAL;
+    if (!ed_batch_in_bounds(blob_len, off, len, n)) return SBFT_GV_EINVAL;
+    std::vector<std::vector<uint64_t>> rebased(ctx->slots.size() + 1);
+    return run_chunks(ctx, n, [&](const Chunk& c, size_t i) {
+        return enqueue_ed25519(c, blob, blob_len, off, len, nullptr, nullptr, dig_out, rebased[i]);
+    });
+}
+
+int sbft_gv_selftest_ed25519(sbft_gv_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, size_t n,
+                             uint8_t* out) {
+    if (!ctx) return SBFT_GV_EINVAL;
+    if (n == 0) return SBFT_GV_OK;
+    if (!a || !b || !out || op < 0 || op > SBFT_GV_ED_OP_DOUBLE_SCALAR || n > 0xffffffffu) return SBFT_GV_EINVAL;
+    return run_chunks(ctx, n, [&](const Chunk& c, size_t) { return enqueue_selftest_ed25519(c, op, a, b, out); });
 }
 
 int sbft_gv_sha256_verify_p256(sbft_gv_ctx* ctx, const uint8_t* blob, size_t blob_len,

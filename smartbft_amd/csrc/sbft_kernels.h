@@ -91,6 +91,27 @@ int sbft_launch_selftest(int op, const uint8_t* d_a, const uint8_t* d_b, uint8_t
 }
 
 extern "C" {
+// Ed25519 (ed25519_verify.hip). Messages are blob[off[k], off[k] + len[k]) at any byte alignment;
+// the kernels read only the aligned 4-byte words that hold a message byte, so the blob needs no
+// slack past its last message. d_sig (n x 64 B, R || S), d_pub (n x 32 B) and d_dig are 4-byte
+// aligned.
+// bytes of device workspace one sbft_launch_ed25519_verify call of n tuples needs (the per-lane
+// tables of A's multiples; private to the stream)
+size_t sbft_ed25519_work_bytes(size_t n);
+int sbft_launch_ed25519_verify(const uint8_t* d_blob, const uint64_t* d_off, const uint32_t* d_len,
+                               const uint8_t* d_sig, const uint8_t* d_pub, uint8_t* d_ok, uint32_t n,
+                               void* d_work, hipStream_t stream);
+// SHA-512 of n messages, one lane each -> n x 64-byte digests
+int sbft_launch_sha512(const uint8_t* d_blob, const uint64_t* d_off, const uint32_t* d_len, uint8_t* d_dig,
+                       uint32_t n, hipStream_t stream);
+// Element-wise self-test of the Ed25519 primitives (op codes at ed25519_selftest_kernel);
+// d_work: sbft_ed25519_selftest_work_bytes(n) bytes
+size_t sbft_ed25519_selftest_work_bytes(size_t n);
+int sbft_launch_ed25519_selftest(int op, const uint8_t* d_a, const uint8_t* d_b, uint8_t* d_out, uint32_t n,
+                                 void* d_work, hipStream_t stream);
+}
+
+extern "C" {
 // Registered-key (comb table) path, p256_keyed.hip.
 size_t sbft_comb_table_bytes(void);
 // table[w][j] = j 2^(8w) Q for the key (qx, qy) (32-byte big-endian, device memory);

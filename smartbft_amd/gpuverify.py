@@ -25,6 +25,7 @@ EXPORTS = [
     "sbft_gv_sha256_verify_p256_framed", "sbft_gv_host_alloc", "sbft_gv_host_free",
     "sbft_gv_plan_split", "sbft_gv_sha256_verify_p256_stream", "sbft_gv_inject_fault",
     "sbft_gv_register_client_keys", "sbft_gv_verify_p256_kernel",
+    "sbft_gv_verify_ed25519", "sbft_gv_verify_ed25519_dev", "sbft_gv_sha512", "sbft_gv_selftest_ed25519",
 ]
 
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -32,6 +33,9 @@ _vp = ctypes.c_void_p
 
 # sbft_gv_verify_p256_kernel's kernel names (include/sbft_gpuverify.h)
 KERNEL_EXACT, KERNEL_THROUGHPUT, KERNEL_PAIR, KERNEL_HALF, KERNEL_HALF_WIDE = 0, 1, 2, 3, 4
+# sbft_gv_selftest_ed25519's op codes (SBFT_GV_ED_OP_*)
+(ED_OP_FE_MUL, ED_OP_FE_SQR, ED_OP_FE_INVERT, ED_OP_DECODE, ED_OP_SC_REDUCE, ED_OP_BASE_MULT,
+ ED_OP_DOUBLE_SCALAR) = range(7)
 
 
 class GpuVerifyError(RuntimeError):
@@ -110,6 +114,11 @@ def load_library():
     _szp = ctypes.POINTER(ctypes.c_size_t)
     L.sbft_gv_plan_split.argtypes = [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, _szp, _szp]
     L.sbft_gv_plan_split.restype = ctypes.c_size_t
+    L.sbft_gv_verify_ed25519.argtypes = [_vp, _u8p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), _u32p,
+                                         _u8p, _u8p, ctypes.c_size_t, _u8p]
+    L.sbft_gv_verify_ed25519_dev.argtypes = [_vp, ctypes.c_int] + [_vp] * 5 + [ctypes.c_size_t, _vp, _vp]
+    L.sbft_gv_sha512.argtypes = L.sbft_gv_sha256.argtypes
+    L.sbft_gv_selftest_ed25519.argtypes = L.sbft_gv_selftest_field.argtypes
     _LIB = L
     return L
 
@@ -470,6 +479,72 @@ class GpuVerifier:
             self.ctx, d_ok.device.index, d_blob.data_ptr(), _dev(d_off, n, "offsets", d_off.dtype),
             _dev(d_len, n, "lengths", d_len.dtype), None, *p, n, _dev(d_ok, n, "ok"),
             _dev(d_dig, 32 * n, "digests"), self._stream(stream, d_ok.device)), "sbft_gv_sha256_verify_p256_dev")
+
+    # ---- Ed25519 (crypto/ed25519.Verify semantics; include/sbft_gpuverify.h) ----
+    @staticmethod
+    def _ed_rows(sig, pub, n: int):
+        sig = np.ascontiguousarray(np.asarray(sig, dtype=np.uint8))
+        pub = np.ascontiguousarray(np.asarray(pub, dtype=np.uint8))
+        if sig.shape != (n, 64):
+            raise ValueError(f"signatures: expected ({n}, 64) uint8, got {sig.shape}")
+        if pub.shape != (n, 32):
+            raise ValueError(f"public keys: expected ({n}, 32) uint8, got {pub.shape}")
+        return sig, pub
+
+    def verify_ed25519(self, blob, off, ln, sig, pub) -> np.ndarray:
+        """Batched Ed25519 verify: message k = blob[off[k], off[k] + ln[k]), sig (n, 64) R || S,
+        pub (n, 32). Returns n verdict bytes."""
+        blob, off, ln, n = _msgs(blob, off, ln)
+        sig, pub = self._ed_rows(sig, pub, n)
+        ok = np.zeros(n, dtype=np.uint8)
+        self._check(self.L.sbft_gv_verify_ed25519(
+            self.ctx, _p(blob) if blob.size else None, blob.size,
+            off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ln.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+            _p(sig), _p(pub), n, _p(ok)), "sbft_gv_verify_ed25519")
+        return ok
+
+    def verify_ed25519_dev(self, d_blob, d_off, d_len, d_sig, d_pub, d_ok, stream=None, check: bool = True):
+        """Device-resident Ed25519 verify (sbft_gv_verify_ed25519_dev): enqueues on the stream.
+        The blob needs no padding past its last message. check=True validates offsets + lengths
+        against the blob on the launch stream first (_check_blob_bounds: this synchronises it)."""
+        import torch
+        n = d_ok.numel()
+        if d_blob.dtype != torch.uint8 or not d_blob.is_contiguous() or not d_blob.is_cuda:
+            raise ValueError("blob: expected a contiguous uint8 device tensor")
+        if d_off.dtype not in (torch.int64, torch.uint64):
+            raise ValueError(f"offsets: expected 64-bit integers, got {d_off.dtype}")
+        if d_len.dtype not in (torch.int32, torch.uint32):
+            raise ValueError(f"lengths: expected 32-bit integers, got {d_len.dtype}")
+        p_off = _dev(d_off, n, "offsets", d_off.dtype)
+        p_len = _dev(d_len, n, "lengths", d_len.dtype)
+        p_sig = _dev(d_sig, 64 * n, "signatures")
+        p_pub = _dev(d_pub, 32 * n, "public keys")
+        p_ok = _dev(d_ok, n, "ok")
+        if n and check:
+            self._check_blob_bounds(d_blob, d_off, d_len, stream, d_ok.device)
+        # an empty blob (every message empty) has no storage: any non-NULL address will do
+        p_blob = d_blob.data_ptr() or p_sig
+        self._check(self.L.sbft_gv_verify_ed25519_dev(
+            self.ctx, d_ok.device.index, p_blob, p_off, p_len, p_sig, p_pub, n, p_ok,
+            self._stream(stream, d_ok.device)), "sbft_gv_verify_ed25519_dev")
+
+    def sha512(self, blob, off, ln) -> np.ndarray:
+        blob, off, ln, n = _msgs(blob, off, ln)
+        dig = np.zeros((n, 64), dtype=np.uint8)
+        self._check(self.L.sbft_gv_sha512(self.ctx, _p(blob) if blob.size else None, blob.size,
+                                          off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                          ln.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n, _p(dig)),
+                    "sbft_gv_sha512")
+        return dig
+
+    def selftest_ed25519(self, op: int, a, b) -> np.ndarray:
+        """Element-wise self-test of the Ed25519 primitives (ED_OP_*): a, b (n, 32) little-endian."""
+        n = len(a)
+        a, b = _soa(a, n), _soa(b, n)
+        out = np.zeros((n, 32), dtype=np.uint8)
+        self._check(self.L.sbft_gv_selftest_ed25519(self.ctx, op, _p(a), _p(b), n, _p(out)),
+                    "sbft_gv_selftest_ed25519")
+        return out
 
     def kernel_timing(self, enable: bool):
         """Record HIP events around each device-resident verify's main kernel."""
